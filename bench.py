@@ -2,12 +2,19 @@
 """Headline benchmark: PM-VAE MNIST training images/sec (BASELINE.json metric), per-GPU batch 256.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one full optimizer step of train_pm_vae.py on configs/pm_vae_mnist.py: eps sampling,
 masked-encoder + encoder + decoder forward, ELBO + posterior-matching loss, full backward, Adam.
 Inputs are synthetic batches resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else the line can
+carry: per-step spread, strict-f32 throughput, per-kernel roofline (with rocprofv3 PMC child passes), BASELINE.json's
+other configs (aux.secondary) and the CPU baseline.  --dump-outputs DIR writes the state and metrics the last timed step
+left (parameters, Adam moments, loss terms) as DIR/<name>.npy; the inputs are seeded, so two builds compare file by file.
 """
 import argparse
 import json
@@ -125,6 +132,21 @@ def measured_traffic():
         wkb, wl = write.get(n, (0.0, 1))
         out[n] = int((2.0 * kb / max(launches, 1) + wkb / max(wl, 1)) * 1024)
     return out
+
+
+def dump_outputs(out_dir, model, metrics):
+    """What a caller of the train step receives after the last timed step: the new parameters and Adam moments (float32,
+    one file per named tensor: params.<name>.npy, adam_m.<name>.npy, adam_v.<name>.npy, '/' -> '.') and the loss terms
+    (float64 scalars: loss.npy, kl.npy, ...).  About 25 MB for configs/pm_vae_mnist.py; `metrics` comes from
+    read_metrics(), which has synchronised the step's streams."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for prefix, which in (("params", "p"), ("adam_m", "m"), ("adam_v", "v")):
+        for name, t in model.store.to_dict(which).items():
+            np.save(os.path.join(out_dir, f"{prefix}.{name.replace('/', '.')}.npy"), t.cpu().numpy().astype(np.float32))
+    for name, v in metrics.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.float64(v))
 
 
 def cpu_baseline(cfg, xs, B, budget_s=25.0):
@@ -247,6 +269,11 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (BASELINE: 256)")
     ap.add_argument("--graph", action="store_true", help="replay one captured HIP graph per step (single stream) "
                                                         "instead of eager launches on two overlapping streams")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need (step spread, "
+                                                       "f32 sample, roofline + PMC passes, secondary configs, CPU "
+                                                       "baseline); the --no-* / *-steps options below refine --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (parameters, Adam "
+                                                          "moments, loss terms) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-steps", type=int, default=5, help="eager steps with per-kernel HIP events")
     ap.add_argument("--f32", action="store_true", help="every GEMM on the f32 MFMA (strict-parity mode) instead of the "
@@ -269,6 +296,10 @@ def main():
                     help="weak: the config's per-GPU batch on every rank; strong: BASELINE.json's fixed GLOBAL batch split over "
                          "the ranks (pm_vdvae_mnist 64, pm_vqvae_celeb_a 128: per-GPU 8 / 16 at N = 8)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "pm_vae_mnist" or args.scaling == "strong"):
+        ap.error("--dump-outputs covers the headline workload (pm_vae_mnist, weak scaling) only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` unaided: this parent never touches the GPU; it starts the N ranks as CHILD processes
@@ -301,13 +332,14 @@ def main():
     # BEFORE this process initialises the GPU (counters cannot be read from inside the measured process)
     traffic, traffic_src = None, None
     headline = args.workload == "pm_vae_mnist" and args.scaling == "weak"
+    profile = args.full and args.profile_steps > 0          # the roofline pass and what feeds it: --full only
     mfma_busy = None
-    if world == 1 and not args.no_pmc and args.profile_steps > 0 and headline:
+    if world == 1 and not args.no_pmc and profile and headline:
         mfma_busy = pmc_mfma_child()
-    if world == 1 and not args.no_pmc and args.profile_steps > 0 and headline:
+    if world == 1 and not args.no_pmc and profile and headline:
         traffic = measured_traffic()
         traffic_src = "this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE child passes, 2*FETCH_SIZE + WRITE_SIZE per launch"
-    if traffic is None and world == 1 and args.profile_steps > 0:
+    if traffic is None and world == 1 and profile:
         for name in ("r03_final_pmc_traffic.json", "r02_final_pmc_traffic.json", "r01_final_pmc_traffic.json"):
             try:
                 with open(os.path.join(ROOT, "profiles", name)) as fp:
@@ -389,10 +421,11 @@ def main():
     gc_guard.__enter__()
     run(ts, args.warmup)
     fence()
-    marks = []
-    with torch.cuda.stream(ts.stream):
-        e0 = ops.Event()
-        e0.record()
+    marks = [] if args.full else None
+    if args.full:
+        with torch.cuda.stream(ts.stream):
+            e0 = ops.Event()
+            e0.record()
     t0 = time.perf_counter()
     run(ts, args.steps, args.warmup, marks)
     fence()
@@ -402,10 +435,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     metrics = ts.read_metrics()
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the same model again (--full's spread steps and profiling pass)
+        dump_outputs(args.dump_outputs, model, metrics)
     # spread of the K timed steps (HIP events on the step's stream, one per step; the headline stays K steps / wall time)
-    per_step = sorted(a.elapsed_ms(b) for a, b in zip([e0] + marks[:-1], marks))
-    spread = {"min": round(per_step[0], 4), "median": round(per_step[len(per_step) // 2], 4),
-              "max": round(per_step[-1], 4)} if per_step else None
+    spread = None
+    if args.full:
+        per_step = sorted(a.elapsed_ms(b) for a, b in zip([e0] + marks[:-1], marks))
+        spread = {"min": round(per_step[0], 4), "median": round(per_step[len(per_step) // 2], 4),
+                  "max": round(per_step[-1], 4)}
     # The driver fixes --steps (20 steps = a 29 ms region): quartiles over `--spread-steps` further steps of the same loop,
     # one HIP event per step on the step's stream, back the A/B claims in DESIGN.md (outside the headline's timed region)
     if spread is not None and args.spread_steps > 0:
@@ -423,7 +461,7 @@ def main():
     gc_guard.__exit__(None, None, None)
     # strict arithmetic (every GEMM on the f32 MFMA) on the same batches: a few steps OUTSIDE the timed region
     f32_ips = None
-    if rank == 0 and world == 1 and not args.f32 and not args.no_f32_aux:
+    if args.full and rank == 0 and world == 1 and not args.f32 and not args.no_f32_aux:
         m32 = PosteriorMatchingVAE.from_config(cfg["model"], device=dev, seed=1)
         m32.init(xs)
         m32.store.use_bf16 = False
@@ -439,7 +477,7 @@ def main():
 
     # live per-kernel timing with HIP events on the launching stream (eager, outside the timed region)
     roofline = None
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and profile:
         model.concurrent = False        # per-kernel times: one stream, so durations do not overlap
         prof = PMVAETrainStep(model, cfg, opt, B, xs, seed=1234, world_size=1, rank=0, use_graph=False)
         prof.set_batch(batches[0]["image"], batches[0]["mask"])
@@ -501,7 +539,7 @@ def main():
 
     # BASELINE.json's other configs on the driver's clock: a few timed steps each, after (outside) the headline's region
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary and not args.f32:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not args.f32:
         from tools.workloads import build, measure
 
         secondary = []
@@ -545,7 +583,7 @@ def main():
                     "hbm_frac": round(per_gpu * B_ALG_F32 / (HBM_PEAK_GBS * 1e9), 4)},
             "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, xs, B)
         else:
             line["cpu_baseline"] = None
