@@ -238,6 +238,9 @@ SIGNATURES = {
     "pm_dmol_ll_fwd": [_P, _P, _P, _P, _LL, _I, _I, _F, _F],
     "pm_dmol_ll_bwd": [_P, _P, _P, _F, _P, _LL, _I, _I, _F, _F],
     "pm_dmol_mean": [_P, _P, _P, _LL, _I, _F, _F],
+    "pm_dmol_mc_ll_fwd": [_P, _P, _P, _P, _LL, _I, _I, _I, _F, _F],
+    "pm_dmol_mc_ll_bwd": [_P, _P, _P, _F, _P, _LL, _I, _I, _I, _F, _F],
+    "pm_dmol_mc_mean": [_P, _P, _P, _LL, _I, _I, _F, _F],
     "pm_vdvae_loss": [_P, _P, _P, _P, _I, _F, _P],
     "pm_sumsq": [_P, _P, _LL, _P],
     "pm_sumsq_det": [_P, _P, _LL, _P, _P],

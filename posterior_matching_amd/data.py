@@ -18,6 +18,8 @@ def data_shape(dataset: str):
         return (28, 28, 1)
     if dataset == "celeb_a":
         return (64, 64, 3)                  # utils.py:76-85: centre crop [45:-45, 25:-25] resized to 64 x 64
+    if dataset == "cifar10":
+        return (32, 32, 3)
     return {"gas": (8,), "power": (6,), "hepmass": (21,), "miniboone": (43,), "bsds": (63,)}[dataset]
 
 
@@ -48,6 +50,8 @@ class SyntheticDataset:
                 x = arrays[idx].astype(np.float32)
             elif self.key == "image" and name == "celeb_a":
                 x = rng.uniform(size=(batch_size,) + shape).astype(np.float32)     # U[0, 1] RGB
+                if not normalize_images:                 # raw 0..255 pixel values
+                    x = np.round(x * 255.0).astype(np.float32)
             elif self.key == "image":
                 # MNIST-like: ~19 % of the pixels carry ink, values in [0, 1] (utils.py:50-54: x / 255)
                 x = (rng.uniform(size=(batch_size,) + shape) * (rng.uniform(size=(batch_size,) + shape) < 0.19)).astype(np.float32)

@@ -618,8 +618,8 @@ class PosteriorMatchingVDVAE(Module):
                  seed: int = 1):
         super().__init__(name)
         image_shape = tuple(image_shape)
-        if image_shape[-1] != 1:
-            raise NotImplementedError("LogisticMixture with num_channels > 1 (channel coefficients) has no HIP path")
+        if image_shape[-1] not in (1, 2, 3, 4):
+            raise NotImplementedError(f"LogisticMixture with num_channels = {image_shape[-1]}: the HIP path has 1 to 4 channels")
         if custom_width_string:
             raise NotImplementedError("custom_width_string has no HIP path")
         self.config = dict(image_shape=image_shape, encoder_blocks=encoder_blocks, decoder_blocks=decoder_blocks,
@@ -661,7 +661,8 @@ class PosteriorMatchingVDVAE(Module):
         mid = int(width * c["bottleneck_multiple"])
         self.encoder.ws = self.masked_encoder.ws = ws
         self.encoder.build(store, "encoder", (H, W_, C))
-        self.masked_encoder.build(store, "masked_encoder", (H, W_, 2 * C))
+        # the masked encoder sees concat([x_normalised * b, b]) with a one-channel mask b (masking.py:338-348): C + 1 channels
+        self.masked_encoder.build(store, "masked_encoder", (H, W_, C + 1))
         spec = parse_layer_string(c["decoder_blocks"])
         self.dec_blocks = [PosteriorMatchingDecoderBlock(store, ws, f"decoder/block_{i}", Z, r, m, len(spec), width, mid)
                            for i, (r, m) in enumerate(spec)]
@@ -670,7 +671,7 @@ class PosteriorMatchingVDVAE(Module):
         for r in self.bias_res:
             store.add(f"decoder/x_bias_{r}", (1, r, r, width))      # reference name: "x_bias_{res}]" (stray bracket, :797)
         nm = c["num_mixtures"]
-        self.out_net = _Conv(store, "decoder/out_net", LayerGeom.conv(H, W_, width, nm * 3, 1, 1, "SAME"), width)
+        self.out_net = _Conv(store, "decoder/out_net", LayerGeom.conv(H, W_, width, nm * self.dmol_fields, 1, 1, "SAME"), width)
         store.add("decoder/gain", (1, 1, 1, width), fan_in=-3)      # Constant(1.0)
         store.add("decoder/bias", (1, 1, 1, width))
         store.allocate(device, self._seed if seed is None else seed)
@@ -682,23 +683,43 @@ class PosteriorMatchingVDVAE(Module):
     def num_params(self) -> int:
         return self.store.num_params
 
+    @property
+    def dmol_fields(self) -> int:
+        """parameters per mixture component of LogisticMixture(num_channels=C) (:449-476): 2C + C(C-1)/2 + 1"""
+        C = self.config["image_shape"][-1]
+        return 2 * C + C * (C - 1) // 2 + 1
+
+    def _dmol_ll(self, params, x, ll, P: int) -> None:
+        nm = self.config["num_mixtures"]
+        if x.shape[-1] == 1:
+            ops.dmol_ll_fwd(params, x, ll, nm, P)
+        else:
+            ops.dmol_mc_ll_fwd(params, x, ll, nm, P)
+
+    def _dmol_mean(self, params, out) -> None:
+        nm = self.config["num_mixtures"]
+        if out.shape[-1] == 1:
+            ops.dmol_mean(params, out, nm)
+        else:
+            ops.dmol_mc_mean(params, out, nm)
+
     def eps_shapes(self, B: int) -> List[Tuple[int, ...]]:
         Z = self.config["latent_dim"]
         return [(B, blk.base, blk.base, Z) for blk in self.dec_blocks]
 
     def __call__(self, x: torch.Tensor, b: torch.Tensor, eps: Sequence[torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """reference vdvae.py:76-94.  x: raw pixel values 0..255 [B,H,W,1]; b: mask (1 = observed);
+        """reference vdvae.py:76-94.  x: raw pixel values 0..255 [B,H,W,C]; b: mask [B,H,W,1] (1 = observed);
         eps: one N(0,1) draw [B,res,res,Z] per decoder block (the caller owns the RNG).  Returns per-example
         reconstruction_ll, kl, pm_kl (device tensors owned by the model)."""
         if self.store is None:
             self.init(x.device)
         c = self.config
-        B, H, W_, _ = x.shape
+        B, H, W_, C = x.shape
         width, nm = c["width"], c["num_mixtures"]
         self._B, self._x = B, x
         xn = self.ws.get("vdvae/xn", tuple(x.shape))
         ops.scale_shift(x, 1.0 / 127.5, -1.0, xn)
-        xob = self.ws.get("vdvae/x_o_b", (B, H, W_, 2))
+        xob = self.ws.get("vdvae/x_o_b", (B, H, W_, C + 1))
         ops.mask_concat(xn, b, xob)
         streams = self._branch_streams(x.device)
         main = torch.cuda.current_stream(x.device)
@@ -740,12 +761,12 @@ class PosteriorMatchingVDVAE(Module):
         px_z = self.ws.get("decoder/px_z", tuple(top.shape))
         ops.affine_fwd(top, self.store.p["decoder/gain"], self.store.p["decoder/bias"], px_z)
         self._px_z = px_z
-        params = self.ws.get("decoder/dmol_params", (B, H, W_, 3 * nm))
+        params = self.ws.get("decoder/dmol_params", (B, H, W_, self.dmol_fields * nm))
         ops.layer_forward(self.out_net.g, px_z, self.store.p[self.out_net.w], self.store.p[self.out_net.b], params,
                           wsplit=self.store.split_view(self.out_net.ws_f))
         self._params = params
         rec = self.ws.get("vdvae/rec_ll", (B,))
-        ops.dmol_ll_fwd(params, x, rec, nm, H * W_)
+        self._dmol_ll(params, x, rec, H * W_)
         ops.vdvae_loss(rec, kl, pm_kl, float(H * W_ * c["image_shape"][-1]), self.metrics)
         return {"reconstruction_ll": rec, "kl": kl, "pm_kl": pm_kl}
 
@@ -770,7 +791,7 @@ class PosteriorMatchingVDVAE(Module):
         nm = c["num_mixtures"]
         xn = self.ws.get("vdvae/xn", tuple(x.shape))
         ops.scale_shift(x, 1.0 / 127.5, -1.0, xn)
-        xob = self.ws.get("vdvae/x_o_b", (B, H, W_, 2))
+        xob = self.ws.get("vdvae/x_o_b", (B, H, W_, C + 1))
         ops.mask_concat(xn, b, xob)
         macts = self.masked_encoder(xob)                    # identical for every sample: the scan body is deterministic in it
         out = torch.empty((B, num_samples, H, W_, C), device=x.device)
@@ -792,10 +813,10 @@ class PosteriorMatchingVDVAE(Module):
                 xs[r] = blk.forward_partial(x_in, macts[r], e)
             px_z = self.ws.get("decoder/px_z", tuple(xs[H].shape))
             ops.affine_fwd(xs[H], self.store.p["decoder/gain"], self.store.p["decoder/bias"], px_z)
-            params = self.ws.get("decoder/dmol_params", (B, H, W_, 3 * nm))
+            params = self.ws.get("decoder/dmol_params", (B, H, W_, self.dmol_fields * nm))
             ops.layer_forward(self.out_net.g, px_z, self.store.p[self.out_net.w], self.store.p[self.out_net.b], params,
                               wsplit=self.store.split_view(self.out_net.ws_f))
-            ops.dmol_mean(params, mean, nm)
+            self._dmol_mean(params, mean)
             out[:, s].copy_(mean)
         ops.impute_blend(x, b, out, 1.0, 0.0)               # jnp.where(b == 1, x, mean): no clipping
         return out
@@ -823,11 +844,11 @@ class PosteriorMatchingVDVAE(Module):
             xs[r] = blk.forward_prior(x_in, e)
         px_z = self.ws.get("decoder/px_z", tuple(xs[H].shape))
         ops.affine_fwd(xs[H], self.store.p["decoder/gain"], self.store.p["decoder/bias"], px_z)
-        params = self.ws.get("decoder/dmol_params", (N, H, W_, 3 * nm))
+        params = self.ws.get("decoder/dmol_params", (N, H, W_, self.dmol_fields * nm))
         ops.layer_forward(self.out_net.g, px_z, self.store.p[self.out_net.w], self.store.p[self.out_net.b], params,
                           wsplit=self.store.split_view(self.out_net.ws_f))
         out = torch.empty((N, H, W_, C), device=dev)
-        ops.dmol_mean(params, out, nm)
+        self._dmol_mean(params, out)
         return out
 
     def is_log_probs(self, x: torch.Tensor, b: torch.Tensor, num_samples: int = 100, seed: int = 0,
@@ -843,7 +864,7 @@ class PosteriorMatchingVDVAE(Module):
         S, nm, Z = int(num_samples), c["num_mixtures"], c["latent_dim"]
         xn = self.ws.get("vdvae/xn", tuple(x.shape))
         ops.scale_shift(x, 1.0 / 127.5, -1.0, xn)
-        xob = self.ws.get("vdvae/x_o_b", (B, H, W_, 2))
+        xob = self.ws.get("vdvae/x_o_b", (B, H, W_, C + 1))
         ops.mask_concat(xn, b, xob)
         acts = self.encoder(xn)
         macts = self.masked_encoder(xob)
@@ -872,11 +893,11 @@ class PosteriorMatchingVDVAE(Module):
                 xs[r] = blk.forward_lls(x_in, acts[r], macts[r], e, em, stats)
             px_z = self.ws.get("decoder/px_z", tuple(xs[H].shape))
             ops.affine_fwd(xs[H], self.store.p["decoder/gain"], self.store.p["decoder/bias"], px_z)
-            params = self.ws.get("decoder/dmol_params", (2 * B, H, W_, 3 * nm))
+            params = self.ws.get("decoder/dmol_params", (2 * B, H, W_, self.dmol_fields * nm))
             ops.layer_forward(self.out_net.g, px_z, self.store.p[self.out_net.w], self.store.p[self.out_net.b], params,
                               wsplit=self.store.split_view(self.out_net.ws_f))
-            ops.dmol_ll_fwd(params[:B], x, lls[0, s], nm, H * W_)
-            ops.dmol_ll_fwd(params[B:], x, pix, nm, 1)                               # log_prob(x, independent=False)
+            self._dmol_ll(params[:B], x, lls[0, s], H * W_)
+            self._dmol_ll(params[B:], x, pix, 1)                                     # log_prob(x, independent=False)
             ops.segment_wsum(pix, b, lls[1, s])                                      # sum over the observed pixels
             # px = pxz_ll + pz - qzx ; pxo = pxoz_ll + masked_pz - masked_qzx   (:134-140)
             ops.scale_shift(stats["qzx"], -1.0, 0.0, comb[0, s])
@@ -894,9 +915,9 @@ class PosteriorMatchingVDVAE(Module):
 
     def reconstruction(self) -> torch.Tensor:
         """decoder_dist.mean() of the last call (reference :93)"""
-        B, H, W_, _ = self._x.shape
-        out = torch.empty((B, H, W_, 1), device=self._x.device)
-        ops.dmol_mean(self._params, out, self.config["num_mixtures"])
+        B, H, W_, C = self._x.shape
+        out = torch.empty((B, H, W_, C), device=self._x.device)
+        self._dmol_mean(self._params, out)
         return out
 
     def backward(self, grad_scale: float = 1.0) -> None:
@@ -925,7 +946,10 @@ class PosteriorMatchingVDVAE(Module):
         import os
 
         dparams = self.ws.get("decoder/d_dmol_params", tuple(self._params.shape))
-        ops.dmol_ll_bwd(self._params, self._x, -g, dparams, nm, H * W_)
+        if self._x.shape[-1] == 1:
+            ops.dmol_ll_bwd(self._params, self._x, -g, dparams, nm, H * W_)
+        else:
+            ops.dmol_mc_ll_bwd(self._params, self._x, -g, dparams, nm, H * W_)
         self.wgrad(self.out_net.g, self._px_z, dparams, self.store.g[self.out_net.w], self.store.g[self.out_net.b])
         if self.store.reducer is not None and self.ws.wgrad_batch is None:     # (batched: the flush reports it)
             self.ws.join_all_aux()

@@ -1558,6 +1558,22 @@ def dmol_mean(params, out, nm: int, low: float = 0.0, high: float = 255.0) -> No
     _call("pm_dmol_mean", _ptr(params), _ptr(out), out.numel(), nm, low, high)
 
 
+def dmol_mc_ll_fwd(params, value, ll, nm: int, P: int, low: float = 0.0, high: float = 255.0) -> None:
+    """C = value.shape[-1] in 2..4 channels: params [..., nm * (2C + C(C-1)/2 + 1)], value [..., C]; ll[rows / P]"""
+    C_ = value.shape[-1]
+    _call("pm_dmol_mc_ll_fwd", _ptr(params), _ptr(value), _ptr(ll), value.numel() // C_, C_, nm, P, low, high)
+
+
+def dmol_mc_ll_bwd(params, value, g: float, dparams, nm: int, P: int, low: float = 0.0, high: float = 255.0) -> None:
+    C_ = value.shape[-1]
+    _call("pm_dmol_mc_ll_bwd", _ptr(params), _ptr(value), g, _ptr(dparams), value.numel() // C_, C_, nm, P, low, high)
+
+
+def dmol_mc_mean(params, out, nm: int, low: float = 0.0, high: float = 255.0) -> None:
+    C_ = out.shape[-1]
+    _call("pm_dmol_mc_mean", _ptr(params), _ptr(out), out.numel() // C_, C_, nm, low, high)
+
+
 def vdvae_loss(rec, kl, pm_kl, num_dims: float, out) -> None:
     _call("pm_vdvae_loss", _ptr(rec), _ptr(kl), _ptr(pm_kl), rec.numel(), num_dims, _ptr(out))
 
