@@ -132,6 +132,8 @@ SIGNATURES = {
     "pm_gather_gemm_bf16_sk": [_P, C.POINTER(GatherDesc), _P, _P, _P, _P, _P, _P, _P, _I, _P, C.c_longlong],
     "pm_gather_gemm_bf16_insum": [_P, C.POINTER(GatherDesc), _P, _P, _P, _P, _P, _P, _P],
     "pm_image_conv_insum_applies": [C.POINTER(GatherDesc)],
+    "pm_conv_stack_plan": [C.POINTER(GatherDesc), _I, C.POINTER(C.c_longlong)],
+    "pm_conv_stack_fwd_bf16": [_P, C.POINTER(GatherDesc), _I, _P, _P, _P, _P, _P],
     "pm_split_weights": [_P, _P, _P, _P, _I, _I],
     "pm_gather_wgrad_bf16": [_P, C.POINTER(GatherDesc), _P, _P, _P, _P],
     "pm_gather_wgrad_table": [_P, C.POINTER(GatherDesc), _P, _P, _P, _P, _P, _I, _I],

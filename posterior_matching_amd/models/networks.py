@@ -46,7 +46,20 @@ class ConvEncoder(Module):
         self._x = x
         self._outs = []
         h = x.t
-        for i, g in enumerate(self.geoms):
+        first = 0
+        ws = [self.store.split_view(self._ws[i][0]) for i in range(min(4, len(self.geoms)))]
+        biases = [self.P(f"conv_{i}/b") for i in range(len(ws))]
+        if (len(ws) == 4 and all(w is not None for w in ws[1:]) and all(b.data_ptr() % 16 == 0 for b in biases)
+                and ops.conv_stack_applies(self.geoms[:4], B)):
+            # the first four layers in one launch, activations resident in LDS (csrc/pm_conv_stack.hip): the same bits as the
+            # layer-wise launches (whose image-resident form needs 16-byte aligned biases for its TR epilogue, too)
+            outs = [self.buf(f"out_{i}", (B, g.OH, g.OW, g.CO)) for i, g in enumerate(self.geoms[:4])]
+            ops.conv_stack_fwd(self.geoms[:4], h, self.P("conv_0/w"), biases[0], ws[1:], biases[1:], outs)
+            self._outs.extend(outs)
+            h = outs[3]
+            first = 4
+        for i in range(first, len(self.geoms)):
+            g = self.geoms[i]
             out = self.buf(f"out_{i}", (B, g.OH, g.OW, g.CO))
             ops.layer_forward(g, h, self.P(f"conv_{i}/w"), self.P(f"conv_{i}/b"), out, out_act=ACT_LEAKY,
                               wsplit=self.store.split_view(self._ws[i][0]))

@@ -731,6 +731,55 @@ def layer_forward(g: LayerGeom, x, w, b, out, in_act=ACT_NONE, out_act=ACT_NONE,
             gelu_fwd(out, None, out2)
 
 
+def _conv_stack_descs(geoms, B: int):
+    descs = (GatherDesc * 4)()
+    for i, g in enumerate(geoms):
+        d = g._desc(B, "fwd")
+        d.in_act, d.out_act = ACT_NONE, ACT_LEAKY
+        descs[i] = d
+    return descs
+
+
+def conv_stack_lds(geoms, B: int) -> Optional[int]:
+    """LDS bytes of the fused four-layer encoder forward (pm_conv_stack_fwd_bf16) for these layer geometries, or None when
+    they do not qualify (csrc/pm_conv_stack.hip)"""
+    if len(geoms) != 4:
+        return None
+    n = C.c_longlong(0)
+    if _lib.load().pm_conv_stack_plan(_conv_stack_descs(geoms, B), 4, C.byref(n)) != 0:
+        return None
+    return n.value
+
+
+def conv_stack_applies(geoms, B: int) -> bool:
+    """The dispatch rule of ConvEncoder: the fused launch replaces the layer-wise launches when the planner accepts the first
+    four layers and the batch is one the layer-wise path runs on the image-resident form (B >= 128, plan_image in
+    csrc/pm_conv.hip) - that form is what the fused kernel reproduces bit for bit; smaller batches run other layer-wise forms.
+    PM_NO_CONV_STACK=1: always the layer-wise path (A/B switch)."""
+    if os.environ.get("PM_NO_CONV_STACK") or B < 128:
+        return False
+    return conv_stack_lds(geoms, B) is not None
+
+
+def conv_stack_fwd(geoms, x, w0, b0, wsplits, biases, outs) -> None:
+    """out_i = leaky(conv_i(out_{i-1})) for the four layers `geoms` in one launch (csrc/pm_conv_stack.hip).  w0 / b0: layer
+    0's f32 weights and bias; wsplits / biases: the forward pre-split copies and the biases of layers 1..3; outs: four
+    [B, OH, OW, CO] tensors."""
+    B = x.shape[0]
+    descs = _conv_stack_descs(geoms, B)
+    for t in outs:
+        _ptr(t)                                                   # contiguity / dtype checks
+    ws = (C.c_void_p * 4)(None, *[w.data_ptr() for w in wsplits])
+    bs = (C.c_void_p * 4)(*[_ptr(b) for b in [b0] + list(biases)])
+    os_ = (C.c_void_p * 4)(*[_ptr(t) for t in outs])
+    work = None
+    if _timer is not None:
+        work = {"flops": sum(_algorithmic_flops(d) for d in descs), "bytes": _nbytes(x, *outs),
+                "detail": " | ".join(_detail(d) for d in descs)}
+    _call("pm_conv_stack_fwd_bf16", descs, 4, _ptr(x), _ptr(w0), ws, bs, os_,
+          tag=f"conv_stack_fwd_bf16_kernel<{geoms[0].CI}, 5, 1, 2, 1>", work=work)
+
+
 def dgrad_insum_ok(g: LayerGeom, B: int, wsplit, force: bool = False) -> bool:
     """True when layer_dgrad(g, dy, ..., in_colsum=db) can also produce db = column sums of dy (the bias gradient of a
     transposed convolution) - its dy images are staged in LDS by the image-resident kernel anyway.  Measured on the PM-VAE step
